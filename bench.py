@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """FaceOff MI355X bench: train frames/s of the VQ-VAE-2 + Conv3d-latent step (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* in the environment), or -- when WORLD_SIZE is not set -- this process starts the N ranks itself
@@ -13,7 +13,9 @@ Workload (BASELINE.json configs[1], "C2"): 256x256, T=5, bs=32 clips per GPU (16
 recon + VQ loss, fp32, synthetic inputs resident in HBM, random-init weights.  A step is one full
 training iteration: forward, fused losses, backward (all 70 gradients), bucketed RCCL gradient
 all-reduce overlapped with backward (N>1), one multi-tensor Adam launch.  Weak scaling: per-GPU work
-is fixed.  Rank 0 prints ONE JSON line.  Besides the headline it carries
+is fixed.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, and `comm` for N > 1).  With --full the line also carries the legs below, each of
+which takes runs of its own (the --no-* options drop single legs of a --full run):
 
   roofline              dominant kernel of the timed (Winograd) step, HIP events per launch
   roofline.direct_conv  the same step on the direct implicit-GEMM kernels (no Winograd): step time + its dominant kernel
@@ -24,6 +26,10 @@ is fixed.  Rank 0 prints ONE JSON line.  Besides the headline it carries
 
 Per-kernel entries (`roofline.kernel`, `kernels`, `c3.kernels`, `c5.kernels`) are keyed by the kernel SYMBOL as rocprofv3 prints it
 (reported by the library: fo_kernel_notes / fo_last_kernel), so a reader can look each one up in profiles/*_kernel_stats.md.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step handed its caller as DIR/<name>.npy (see
+dump_outputs), before any other leg runs.  Inputs and weights are seeded, so two builds run with the same arguments can be compared
+array for array.
 """
 import argparse
 import json
@@ -111,11 +117,48 @@ def cpu_baseline(T, H, W, steps=20, all_cores_budget_s=40):
                       f"{32 * T}-frame step of the GPU workload is not run on the CPU -- its rate is an extrapolation from this sample (the step is linear in clips)"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_CODES = 2 << 20               # code indices per level beyond which a fixed, seeded sample of them is written
+
+
+def dump_outputs(path, eng, trainer, losses):
+    """What the timed step hands its caller, written after the last timed step as path/<name>.npy: the losses it returned
+    (loss_recon, loss_latent, loss_perceptual), the model it trained (state.<key>: parameters and VQ buffers, eng.state_dict()), the
+    gradients of that step (grad.<key>) and its code indices (codes_top / codes_bottom, exact in float32; above DUMP_MAX_CODES a
+    sample at fixed seeded positions, in ascending order).  float32 throughout; at the benchmark's sizes ~37 MB.  A folder this call
+    creates also gets a .gitignore of `*`, as .pytest_cache does, so that a dump inside a checkout leaves its git status clean."""
+    import numpy as np
+    if not os.path.isdir(path):
+        os.makedirs(path)
+        with open(os.path.join(path, ".gitignore"), "w") as fh:
+            fh.write("*\n")
+    torch.cuda.synchronize()
+    arrays = {"loss_recon": losses[0], "loss_latent": losses[1]}
+    if trainer.vqlpips is not None:
+        arrays["loss_perceptual"] = losses[2]
+    arrays.update(("state." + k, v) for k, v in eng.state_dict().items())
+    arrays.update(("grad." + k, v) for k, v in eng.grads.items())
+    arrays["codes_top"], arrays["codes_bottom"] = trainer.last_ids
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if name.startswith("codes_") and a.size > DUMP_MAX_CODES:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_CODES, replace=False))]
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs wrote {total} bytes (limit {DUMP_MAX_BYTES})"
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline (per-kernel roofline and step floor, direct-conv, bf16x6, c3, host-fed, c5, CPU "
+                         "baseline); without it the run only times the headline step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, trained parameters and VQ buffers, gradients, codes) as DIR/<name>.npy")
     ap.add_argument("--clips", type=int, default=32, help="clips per GPU (BASELINE: 32)")
     ap.add_argument("--frames", type=int, default=5, help="frames per clip T (BASELINE: 5)")
     ap.add_argument("--size", type=int, default=256)
@@ -150,7 +193,12 @@ def parse_args(argv=None):
     ap.add_argument("--no-kernel-events", action="store_true", help="skip per-launch HIP-event timing")
     ap.add_argument("--serial-streams", action="store_true",
                     help="run the step without side-stream overlap (what profiles/collect.sh traces: kernels run alone)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:                  # a plain run: the headline step alone
+        args.no_kernel_events = args.no_direct_leg = args.no_x6_leg = args.no_c3 = args.no_h2d_leg = args.no_c5 = args.no_cpu_baseline = True
+    return args
 
 
 def launch_ranks(n, argv):
@@ -378,7 +426,10 @@ def main():
     # ------------------------------------------------------------------ the timed workload
     eng, trainer = make_trainer(winograd=not args.direct_conv, perceptual=args.perceptual, dtype=args.vqvae_dtype)
     issued0 = abi_comm.issued if abi_comm is not None else 0
-    dt, ms_events, (recon, latent, _) = timed(trainer, args.steps, args.warmup)
+    dt, ms_events, losses = timed(trainer, args.steps, args.warmup)
+    recon, latent, _ = losses
+    if args.dump_outputs and rank == 0:            # before any other leg steps this trainer again
+        dump_outputs(args.dump_outputs, eng, trainer, losses)
     comm = None
     if ddp:
         # Self-proving multi-GPU line: how many ranks the process group REALLY had (max-reduced over it), what moved per step,

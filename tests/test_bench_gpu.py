@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_emits_one_valid_json_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--c3-sustained", "6"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--c3-sustained", "6"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -70,11 +70,33 @@ def test_bench_emits_one_valid_json_line():
     assert 0 < x["loss"]["recon"] < 1 and 0 < x["loss"]["latent"] < 1
 
 
+def test_plain_bench_times_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """Without --full: the headline only, exactly --steps timed steps; --dump-outputs writes the last timed step's losses, trained state,
+    gradients and codes as float32 .npy, within 64 MB, and the dumped losses are the ones the line reports."""
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 160 / (d["ms_per_step"] * 1e-3)) < 1e-2 * d["value"]
+    assert not {"roofline", "kernels", "step_floor", "bf16x6", "c3", "h2d_fed", "c5", "cpu_baseline"} & set(d), sorted(d)
+    assert (tmp_path / "out" / ".gitignore").read_text() == "*\n"
+    files = {f.name[:-4]: np.load(f) for f in (tmp_path / "out").glob("*.npy")}
+    assert all(f.dtype == np.float32 for f in files.values()) and sum(f.nbytes for f in files.values()) <= 64 << 20
+    assert sum(k.startswith("state.") for k in files) == 70 + 6 and sum(k.startswith("grad.") for k in files) == 70
+    assert files["codes_top"].size == 160 * 32 * 32 and files["codes_bottom"].size == 160 * 64 * 64 and files["codes_bottom"].max() < 512
+    assert abs(files["loss_recon"].item() - d["loss"]["recon"]) <= 1e-6 and abs(files["loss_latent"].item() - d["loss"]["latent"]) <= 1e-6
+    assert all(np.isfinite(f).all() for f in files.values())
+
+
 def test_bench_multi_gpu_code_path_with_one_rank():
     """The branch the driver's 2/4/8-GPU runs take (RCCL group, bucketed all-reduce, barrier, max over ranks), forced on
     with a single rank: still exactly one JSON line on stdout (RCCL writes its banner to stdout) and a sane value."""
     env = dict(os.environ, FACEOFF_BENCH_FORCE_DDP="1", MASTER_PORT="29577")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                           "--no-kernel-events", "--c3-sustained", "4"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -99,7 +121,7 @@ def test_bench_multi_gpu_code_path_with_one_rank():
 def test_bench_multi_gpu_code_path_over_torch_distributed():
     """--comm torch: the same forced one-rank run with the all-reduces issued through torch.distributed (round 3's path)."""
     env = dict(os.environ, FACEOFF_BENCH_FORCE_DDP="1", MASTER_PORT="29578")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-kernel-events",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-kernel-events",
                           "--no-c3", "--no-c5", "--no-x6-leg", "--no-h2d-leg", "--comm", "torch", "--host-cpus", "2"], capture_output=True, text=True,
                          timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -122,7 +144,7 @@ def test_bench_two_rank_control_flow_on_one_gpu():
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    FACEOFF_BENCH_SHARE_GPU="1", FACEOFF_BENCH_BACKEND="gloo")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--clips", "8",
-                                       "--no-cpu-baseline", "--c3-sustained", "4"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, env=env))
+                                       "--full", "--no-cpu-baseline", "--c3-sustained", "4"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, env=env))
     outs = [p.communicate(timeout=900) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-1500:] for o in outs]
     lines0 = [l for l in outs[0][0].splitlines() if l.strip()]

@@ -37,15 +37,13 @@ print("IMPORTS_OK")
     assert out.returncode == 0 and "IMPORTS_OK" in out.stdout, out.stderr[-2000:]
 
 
-def test_utils_shim_exports_every_name_the_reference_utils_defines(tmp_path):
-    """`from utils import *` (train_faceoff_perceptual.py:17) must hand the trainers every function utils.py defines:
-    validation() calls save_frames_as_video at its first clip (:79), the disc trainers call save_image."""
-    names = ["save_frames_as_video", "save_image", "process_data", "get_facetranslation_latent_conv_perceptual", "get_loaders_and_models"]
-    ref = "/root/reference/utils.py"
-    if os.path.exists(ref):                       # live where the reference exists: its own list of top-level functions
-        import ast
-        names = [n.name for n in ast.parse(open(ref).read()).body if isinstance(n, ast.FunctionDef)]
-        assert "save_frames_as_video" in names and "save_image" in names
+def test_utils_shim_exports_every_name_the_reference_utils_defines(tmp_path, golden_dir):
+    """`from utils import *` (train_faceoff_perceptual.py:17) must hand the trainers every function utils.py defines
+    (the reference's own list of top-level functions, tests/golden/ref_host.json): validation() calls save_frames_as_video at its
+    first clip (:79), the disc trainers call save_image."""
+    import json
+    names = json.load(open(os.path.join(golden_dir, "ref_host.json")))["utils_functions"]
+    assert "save_frames_as_video" in names and "save_image" in names
     code = r"""
 import sys
 sys.path.insert(0, %r)

@@ -73,7 +73,7 @@ def test_product_path_refuses_cpu():
         m(torch.zeros(2, 6, 64, 64))
 
 
-def test_cycle_scheduler_restatement():
+def test_cycle_scheduler_restatement(golden_dir):
     """CycleScheduler (reference scheduler.py:251-320, as configured at train_faceoff_perceptual.py:194-201)."""
     from faceoff_amd.scheduler import CycleScheduler
 
@@ -92,26 +92,20 @@ def test_cycle_scheduler_restatement():
         want.append(end + (lr - end) / 2 * (np.cos(np.pi * i / (n_iter - warm)) + 1))
     np.testing.assert_allclose(got, want, rtol=1e-12)
     assert Opt.param_groups[0]["lr"] == got[-1]
-    ref_path = "/root/reference/scheduler.py"
-    if os.path.exists(ref_path):                        # live cross-check where the reference exists
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("ref_scheduler", ref_path)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        o = Opt()
-        r = mod.CycleScheduler(o, lr, n_iter=n_iter, momentum=None, warmup_proportion=0.05)
-        np.testing.assert_allclose([r.step()[0] for _ in range(n_iter)], got, rtol=1e-12)
-        # default arguments (momentum cycling through betas[0] / momentum, 30 % warm-up), over two and a half cycles
-        for groups in ([{"lr": 0.0, "betas": (0.9, 0.999)}], [{"lr": 0.0, "momentum": 0.9}]):
-            class A:
-                param_groups = [dict(g) for g in groups]
+    # against the reference's own CycleScheduler, as recorded by tests/golden/make_golden_pins.py
+    import json
+    ref = json.load(open(os.path.join(golden_dir, "ref_host.json")))
+    np.testing.assert_allclose(ref["scheduler_warmup_cosine"], got, rtol=1e-12)
+    # default arguments (momentum cycling through betas[0] / momentum, 30 % warm-up), over two and a half cycles
+    for case in ref["scheduler_defaults"]:
+        groups = [{k: tuple(v) if k == "betas" else v for k, v in g.items()} for g in case["groups"]]
 
-            class B:
-                param_groups = [dict(g) for g in groups]
-            mine, ref = CycleScheduler(A(), 1e-3, n_iter=37), mod.CycleScheduler(B(), 1e-3, n_iter=37)
-            for _ in range(93):
-                assert mine.step() == ref.step()
-                assert A.param_groups == B.param_groups
+        class A:
+            param_groups = [dict(g) for g in groups]
+        mine = CycleScheduler(A(), 1e-3, n_iter=37)
+        for want_step, want_groups in case["steps"]:
+            assert list(mine.step()) == want_step
+            assert json.loads(json.dumps(A.param_groups)) == want_groups
 
 
 def test_bucket_plan_covers_arena_in_backward_order():

@@ -57,7 +57,7 @@ def main():
     base = None
     for n in ns:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", str(args.steps), "--warmup", str(args.warmup),
-               "--no-cpu-baseline", "--no-x6-leg", "--no-direct-leg", "--no-h2d-leg"]
+               "--full", "--no-cpu-baseline", "--no-x6-leg", "--no-direct-leg", "--no-h2d-leg"]
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True)
         lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
         if r.returncode != 0 or len(lines) != 1:

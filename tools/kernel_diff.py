@@ -6,7 +6,7 @@ import os
 import subprocess
 import sys
 
-ARGS = "--perceptual --vqvae-dtype bf16 --steps 6 --warmup 2 --no-cpu-baseline --no-c3 --no-x6-leg --no-direct-leg --no-c5 --no-h2d-leg".split()
+ARGS = "--perceptual --vqvae-dtype bf16 --steps 6 --warmup 2 --full --no-cpu-baseline --no-c3 --no-x6-leg --no-direct-leg --no-c5 --no-h2d-leg".split()
 
 
 def run(extra):
